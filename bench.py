@@ -16,6 +16,10 @@ run also MEASURES the second half of BASELINE.json's metric, the wall time of on
 D2H, NCD assembly -- strong scaling), and times the CPU baselines.  ``--mode strong`` makes the matrix
 run the reported value instead.
 
+``--dump-outputs DIR`` writes what the last timed step computed -- the frame sizes of its tile of pairs and the matrix rows
+the tile covers -- as ``DIR/<name>.npy`` (float64), so that two builds can be compared output for output; the inputs are
+generated from fixed seeds and are the same from run to run.
+
 ``--codec gzip|zlib`` measures the deflate path the same way; the default and
 the headline metric is lz4.
 
@@ -257,6 +261,27 @@ def secondary_leg(name, genomes, codec, local_rank, dev, R, steps, opts, data_ke
                          "traffic": traffic, "traffic_source": traffic_src}}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays, seed=20261015):
+    """Write each array as directory/<name>.npy (float32 / float64 as given).  An array that would take the total past
+    64 MB is replaced by a fixed, seeded sample of its elements (flat indices sorted, saved beside it as <name>_index.npy)."""
+    os.makedirs(directory, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if a.nbytes > budget // 2:
+            k = max(1, budget // 2 // (a.itemsize + 8))
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=min(k, a.size), replace=False))
+            np.save(os.path.join(directory, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+            budget -= idx.size * 8
+        np.save(os.path.join(directory, name + ".npy"), a)
+        budget -= a.nbytes
+
+
 def write_fasta_files(directory, genomes, width=80):
     """One single-record FASTA file per genome, 80-column lines, without a Python loop per line."""
     os.makedirs(directory, exist_ok=True)
@@ -440,7 +465,11 @@ def main():
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the short secondary legs behind the headline region (markov / related / soft-masked 5 %% data, gzip, zlib)")
     ap.add_argument("--secondary-steps", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -600,6 +629,13 @@ def main():
     if world > 1:                                       # every rank's tile must be in its slot of the gather
         gather_ok = sdist.allgather_check(gathered[last_slot].cpu() if rehearse else gathered[last_slot],
                                           tile.cpu() if rehearse else tile, rank, world)
+
+    if args.dump_outputs and rank == 0:
+        # the rows of the N x N matrix the last timed step covered (every rank's R rows, in gather order) and their frame sizes
+        off = last_r0 - shard0
+        rows = np.array([r * rows_per_rank + off + i for r in range(world) for i in range(R)], dtype=np.float64)
+        out = gathered[last_slot] if world > 1 else tile
+        dump_outputs(args.dump_outputs, {"pair_rows": rows, "pair_frame_sizes": out.cpu().numpy().view(np.uint32).astype(np.float64)})
 
     # ---- the metric's second half, MEASURED: one full N x N matrix (strong scaling over the ranks) ----
     matrix = None
