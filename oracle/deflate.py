@@ -50,6 +50,11 @@ def lib():
         L.dfl_oracle_window_trace.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t]
         L.dfl_oracle_block_bits.restype = u64
         L.dfl_oracle_block_bits.argtypes = [vp, vp]
+        L.dfl_oracle_block_lengths.restype = None
+        L.dfl_oracle_block_lengths.argtypes = [vp, vp, vp]
+        L.dfl_oracle_block_facts.restype = u64
+        L.dfl_oracle_block_facts.argtypes = [vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t,
+                                             ctypes.POINTER(ctypes.c_size_t)]
         _lib = L
     return _lib
 
@@ -141,3 +146,36 @@ def block_bits(lfreq, dfreq):
     lf = np.ascontiguousarray(lfreq, dtype=np.uint16); df = np.ascontiguousarray(dfreq, dtype=np.uint16)
     assert lf.size == 286 and df.size == 30
     return int(lib().dfl_oracle_block_bits(lf.ctypes.data, df.ctypes.data))
+
+
+# dfl_block_fact / dfl_tree_fact of deflate_oracle.c
+TREE_FACT = np.dtype([("used", "<i4"), ("max_code", "<i4"), ("overflow", "<i4"), ("forced", "<i4"),
+                      ("forced_code", "<i4", (2,))])
+BLOCK_FACT = np.dtype([("opt_len", "<i8"), ("static_len", "<i8"), ("stored_len", "<u8"), ("bits", "<u8"),
+                       ("tree", TREE_FACT, (3,)), ("type", "<i4"), ("tie", "<i4"), ("have_buf", "<i4"),
+                       ("reserved", "<i4")])
+STORED, FIXED, DYNAMIC = 0, 1, 2
+TIE_STATIC, TIE_STORED = 1, 2     # bits of `tie`: static_lenb == dynamic opt_lenb;  stored_len + 4 == opt_lenb
+
+
+def block_lengths(lfreq, dfreq):
+    """zlib's pricing of one histogram (END_BLOCK forced to 1): a BLOCK_FACT record with opt_len, static_len and, per
+    tree (literal/length, distance, bit-length), max_code, the overflow count before the length-limit repair and the
+    forced codes.  The block is priced as one no longer in the window (never stored)."""
+    lf = np.ascontiguousarray(lfreq, dtype=np.uint16); df = np.ascontiguousarray(dfreq, dtype=np.uint16)
+    assert lf.size == 286 and df.size == 30
+    out = np.zeros(1, dtype=BLOCK_FACT)
+    lib().dfl_oracle_block_lengths(lf.ctypes.data, df.ctypes.data, out.ctypes.data)
+    return out[0]
+
+
+def block_facts(x, y=None, level=9):
+    """(raw size, BLOCK_FACT[]): the facts of every block zlib's parse of x (+ y) at `level` closes."""
+    a, b = _arr(x), _arr(y)
+    n = a.size + (b.size if b is not None else 0)
+    facts = np.zeros(n // 16383 + 2, dtype=BLOCK_FACT)
+    nb = ctypes.c_size_t(0)
+    r = lib().dfl_oracle_block_facts(a.ctypes.data, a.size, b.ctypes.data if b is not None else None,
+                                     b.size if b is not None else 0, level, facts.ctypes.data, facts.size,
+                                     ctypes.byref(nb))
+    return int(r), facts[:nb.value]

@@ -97,6 +97,27 @@ typedef struct {
     uint16_t len[HEAP_SIZE];
 } dfl_tree;
 
+/* What zlib's build_tree did for one tree of one block (test facts, never needed for the size itself) */
+typedef struct {
+    int32_t used;            /* symbols of non-zero frequency before any code was forced */
+    int32_t max_code;        /* build_tree's result */
+    int32_t overflow;        /* gen_bitlen's count of nodes deeper than max_length, before the repair (0: no repair) */
+    int32_t forced;          /* codes forced by `while (heap_len < 2)`: 0, 1 or 2 */
+    int32_t forced_code[2];  /* which ones (-1: none) */
+} dfl_tree_fact;
+
+/* One closed block: its trees, its cost in every form, the type chosen and whether a tie decided it */
+typedef struct {
+    int64_t opt_len, static_len;     /* bits without the 3-bit block header, as flush_block has them */
+    uint64_t stored_len;             /* bytes the block covers */
+    uint64_t bits;                   /* bits the block adds to the stream (before the final byte alignment) */
+    dfl_tree_fact tree[3];           /* literal/length, distance, bit-length */
+    int32_t type;                    /* 0 stored, 1 fixed Huffman, 2 dynamic Huffman */
+    int32_t tie;                     /* bit 0: static_lenb == dynamic opt_lenb;  bit 1: stored_len + 4 == opt_lenb */
+    int32_t have_buf;                /* zlib's buf != NULL: the window still holds the block */
+    int32_t reserved;
+} dfl_block_fact;
+
 typedef struct {
     /* input: the virtual concatenation a + b */
     const uint8_t *a, *b;
@@ -125,6 +146,8 @@ typedef struct {
     uint64_t *blk_trace; size_t blk_cap, blk_n;
     uint64_t *win_trace;     /* per block: loop-top stream position << 32 | stream position of window[0] at the flush */
     uint64_t looptop;
+    dfl_block_fact *fact_trace;    /* per block facts (dfl_oracle_block_facts), blk_cap entries */
+    dfl_block_fact fact;           /* those of the block flush_block closed last */
 } dfl_state;
 
 static size_t read_buf(dfl_state *s, uint8_t *dst, size_t size)
@@ -261,10 +284,13 @@ static void pqdownheap(dfl_state *s, dfl_tree *t, int k)
 
 /* build_tree + gen_bitlen.  `slen` = static code lengths (NULL for the bit-length tree). */
 static int build_tree(dfl_state *s, dfl_tree *t, int elems, const int *extra, int extra_base, int max_length,
-                      const uint8_t *slen, int slen_const)
+                      const uint8_t *slen, int slen_const, dfl_tree_fact *fact)
 {
     int n, m, max_code = -1, node, h, bits, overflow = 0;
     uint16_t bl_count[16];
+
+    fact->used = fact->forced = 0;
+    fact->forced_code[0] = fact->forced_code[1] = -1;
 
     s->heap_len = 0;
     s->heap_max = HEAP_SIZE;
@@ -272,8 +298,10 @@ static int build_tree(dfl_state *s, dfl_tree *t, int elems, const int *extra, in
         if (t->freq[n] != 0) { s->heap[++s->heap_len] = max_code = n; s->depth[n] = 0; }
         else t->len[n] = 0;
     }
+    fact->used = s->heap_len;
     while (s->heap_len < 2) {
         node = s->heap[++s->heap_len] = (max_code < 2 ? ++max_code : 0);
+        fact->forced_code[fact->forced++] = node;
         t->freq[node] = 1;
         s->depth[node] = 0;
         s->opt_len--;
@@ -311,6 +339,8 @@ static int build_tree(dfl_state *s, dfl_tree *t, int elems, const int *extra, in
         s->opt_len += (long)t->freq[n] * (bits + xbits);
         if (slen || slen_const) s->static_len += (long)t->freq[n] * ((slen ? slen[n] : slen_const) + xbits);
     }
+    fact->overflow = overflow;
+    fact->max_code = max_code;
     if (overflow > 0) {
         do {
             bits = max_length - 1;
@@ -365,28 +395,41 @@ static void flush_block(dfl_state *s, int have_buf, unsigned long stored_len, in
     int lmax, dmax, max_blindex;
     uint64_t before = s->bits;
 
-    lmax = build_tree(s, &s->lt, L_CODES, extra_lbits, LITERALS + 1, 15, static_llen, 0);
-    dmax = build_tree(s, &s->dt, D_CODES, extra_dbits, 0, 15, NULL, 5);
+    dfl_block_fact *f = &s->fact;
+    lmax = build_tree(s, &s->lt, L_CODES, extra_lbits, LITERALS + 1, 15, static_llen, 0, &f->tree[0]);
+    dmax = build_tree(s, &s->dt, D_CODES, extra_dbits, 0, 15, NULL, 5, &f->tree[1]);
     scan_tree(s, &s->lt, lmax);
     scan_tree(s, &s->dt, dmax);
-    build_tree(s, &s->bt, BL_CODES, extra_blbits, 0, 7, NULL, 0);
+    build_tree(s, &s->bt, BL_CODES, extra_blbits, 0, 7, NULL, 0, &f->tree[2]);
     for (max_blindex = BL_CODES - 1; max_blindex >= 3; max_blindex--)
         if (s->bt.len[bl_order[max_blindex]] != 0) break;
     s->opt_len += 3 * ((long)max_blindex + 1) + 5 + 5 + 4;
 
     opt_lenb = (unsigned long)(s->opt_len + 3 + 7) >> 3;
     static_lenb = (unsigned long)(s->static_len + 3 + 7) >> 3;
+    f->tie = static_lenb == opt_lenb;
     if (static_lenb <= opt_lenb) opt_lenb = static_lenb;
+    f->tie |= (stored_len + 4 == opt_lenb) << 1;
+    f->opt_len = s->opt_len;
+    f->static_len = s->static_len;
+    f->stored_len = stored_len;
+    f->have_buf = have_buf;
+    f->reserved = 0;
 
     if (stored_len + 4 <= opt_lenb && have_buf) {
         s->bits += 3;
         s->bits = (s->bits + 7) & ~(uint64_t)7;
         s->bits += 32 + 8 * (uint64_t)stored_len;
+        f->type = 0;
     } else if (static_lenb == opt_lenb) {
         s->bits += 3 + (uint64_t)s->static_len;
+        f->type = 1;
     } else {
         s->bits += 3 + (uint64_t)s->opt_len;
+        f->type = 2;
     }
+    f->bits = s->bits - before;
+    if (s->fact_trace && s->blk_n < s->blk_cap) s->fact_trace[s->blk_n] = *f;
     if (s->blk_trace && s->blk_n < s->blk_cap) s->blk_trace[s->blk_n] = s->bits - before;
     if (s->win_trace && s->blk_n < s->blk_cap)
         s->win_trace[s->blk_n] = (s->looptop << 32) | (uint64_t)(s->in_pos - s->lookahead - s->strstart);
@@ -581,6 +624,37 @@ uint64_t dfl_oracle_block_bits(const uint16_t *lfreq, const uint16_t *dfreq)
     s->lt.freq[END_BLOCK] = 1;
     flush_block(s, 0, 0, 0);
     r = s->bits;
+    free(s);
+    return r;
+}
+
+/* The pricing of one histogram, with the facts of its three trees: frequencies of the 286 literal/length codes
+ * (END_BLOCK forced to 1, as in dfl_oracle_block_bits) and of the 30 distance codes.  The block counts as one
+ * that is not in the window (no stored block), so out->bits = 3 + min(static, dynamic). */
+void dfl_oracle_block_lengths(const uint16_t *lfreq, const uint16_t *dfreq, dfl_block_fact *out)
+{
+    dfl_state *s = dfl_new(NULL, 0, NULL, 0, 9);
+    if (!s) return;
+    memcpy(s->lt.freq, lfreq, L_CODES * sizeof(uint16_t));
+    memcpy(s->dt.freq, dfreq, D_CODES * sizeof(uint16_t));
+    s->lt.freq[END_BLOCK] = 1;
+    flush_block(s, 0, 0, 0);
+    *out = s->fact;
+    free(s);
+}
+
+/* The facts of every block zlib's parse of a+b at `level` closes, in order (at most `cap`).  Returns the raw
+ * size in bytes; *n_blk receives the number of blocks. */
+uint64_t dfl_oracle_block_facts(const uint8_t *a, size_t na, const uint8_t *b, size_t nb, int level,
+                                dfl_block_fact *facts, size_t cap, size_t *n_blk)
+{
+    uint64_t r;
+    dfl_state *s = dfl_new(a, na, b, nb, level);
+    if (!s) return 0;
+    s->fact_trace = facts; s->blk_cap = cap;
+    deflate_slow(s);
+    r = s->bits >> 3;
+    if (n_blk) *n_blk = s->blk_n;
     free(s);
     return r;
 }
