@@ -251,6 +251,27 @@ int snk_deflate_pairs_device(snk_ctx *ctx, int level, int row_begin, int row_end
  * launch of an asynchronous call to finish); < 0 if unavailable. */
 double snk_deflate_last_ms(snk_ctx *ctx);
 
+/* ---- bzip2 sizes ---------------------------------------------------------
+ * Replace, for the batched path, the codec call bz2.compress(sequence) (libbz2 1.0.8, level 9) of the reference on
+ * the resident sequences.  Sizes are len(bz2.compress(..)) in bytes, bit exact; the caller adds sys.getsizeof's 33.
+ *
+ * snk_bzip2_prepare runs RLE1 and the block cut of every resident sequence once per upload (host threads); the
+ * singles pass keeps, per sequence, the bits of its blocks before the last one, which every pair job with that
+ * sequence as x reuses.  The other calls prepare implicitly.  Layout of the results as for snk_singles / snk_pairs /
+ * snk_pairs_list (item (i, -1) of a list = sequence i alone).  Device scratch is sized by blocks (about 48 blocks of
+ * 900 k RLE1 bytes per batch), not by pairs. */
+int snk_bzip2_prepare(snk_ctx *ctx);
+int snk_bzip2_singles(snk_ctx *ctx, uint32_t *sizes /* [n_seq], host */);
+int snk_bzip2_pairs(snk_ctx *ctx, int row_begin, int row_end, uint32_t *sizes /* host */);
+int snk_bzip2_pairs_list(snk_ctx *ctx, int n_pairs, const int32_t *ij, uint32_t *sizes /* host */);
+/* Same as snk_bzip2_pairs, but the u32 sizes go to DEVICE memory d_sizes ((row_end - row_begin) * n_seq elements)
+ * by a copy queued on `hip_stream` (NULL = the context's stream).  The sizes themselves are computed before the call
+ * returns (the doubling rounds are steered from the host); the copy is not waited for (snk_sync), as for
+ * snk_deflate_pairs_device.  One stream at a time. */
+int snk_bzip2_pairs_device(snk_ctx *ctx, int row_begin, int row_end, void *d_sizes, void *hip_stream);
+/* Device time (ms) of the batches of the last snk_bzip2_pairs / _pairs_list / _pairs_device call. */
+double snk_bzip2_last_ms(snk_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif

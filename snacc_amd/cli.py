@@ -215,6 +215,7 @@ def blocked_sizes(ctx, files, algorithm, reverse_complement, show_progress=False
     if cur:
         groups.append(cur)
     deflate = algorithm in DEFLATE
+    bzip2 = algorithm == "bzip2"
     singles = np.zeros(n, dtype=np.int64)
     pairs = np.zeros((n, n), dtype=np.int64)
 
@@ -240,13 +241,14 @@ def blocked_sizes(ctx, files, algorithm, reverse_complement, show_progress=False
             return
         na = len(ga)
         if gb is None:
-            s = ctx.deflate_singles(algorithm) if deflate else ctx.singles()
+            s = ctx.deflate_singles(algorithm) if deflate else ctx.bzip2_singles() if bzip2 else ctx.singles()
             singles[ga] = s.astype(np.int64) + GETSIZEOF_OVERHEAD
             ij = [(i, j) for i in range(na) for j in range(na)]
         else:
             ij = [(i, na + j) for i in range(na) for j in range(len(gb))]
             ij += [(j, i) for i, j in ij]
-        got = (ctx.deflate_pairs_list(algorithm, ij) if deflate else ctx.pairs_list(ij)).astype(np.int64)
+        got = (ctx.deflate_pairs_list(algorithm, ij) if deflate else ctx.bzip2_pairs_list(ij) if bzip2
+               else ctx.pairs_list(ij)).astype(np.int64)
         for (i, j), v in zip(ij, got):
             pairs[members[i], members[j]] = v + GETSIZEOF_OVERHEAD
 
@@ -291,7 +293,7 @@ def _sum_over_ranks(backend, device):
 
 def gpu_matrix(files, algorithm, reverse_complement, show_progress, save_directory=None, ctx_factory=None,
                backend="nccl"):
-    """Phases A-C for ``-c lz4`` / ``gzip`` / ``zlib`` on the HIP backend.  Returns the float64 NCD
+    """Phases A-C for ``-c lz4`` / ``gzip`` / ``zlib`` / ``bzip2`` on the HIP backend.  Returns the float64 NCD
     matrix in `files` order on rank 0 (None on other ranks).
 
     Under torchrun (WORLD_SIZE > 1) every rank uploads all files, computes its block of rows (blocks of
@@ -323,8 +325,9 @@ def gpu_matrix(files, algorithm, reverse_complement, show_progress, save_directo
         ctx_factory = HipContext
     ctx = ctx_factory(local)
     deflate = algorithm in DEFLATE
-    if deflate or world > 1:
-        # phase A of lz4 (single sizes + prefix snapshots) on demand: a gzip / zlib run never needs it, and a rank of a
+    bzip2 = algorithm == "bzip2"
+    if deflate or bzip2 or world > 1:
+        # phase A of lz4 (single sizes + prefix snapshots) on demand: a gzip / zlib / bzip2 run never needs it, and a rank of a
         # sharded run computes it for its own rows only (the sizes ride on the tile gathers)
         ctx.set_option("defer_singles", 1)
     try:
@@ -355,18 +358,22 @@ def gpu_matrix(files, algorithm, reverse_complement, show_progress, save_directo
         singles = None
         if deflate:
             singles = ctx.deflate_singles(algorithm)
+        elif bzip2:
+            singles = ctx.bzip2_singles()
         elif world == 1:
             singles = ctx.singles()
         if chatty:
             click.secho("Compressing pairs...", fg="green")
         if world > 1:
-            from .distributed import all_pairs_deflate_hip, all_pairs_hip
+            from .distributed import all_pairs_bzip2_hip, all_pairs_deflate_hip, all_pairs_hip
             if backend == "nccl":
                 import torch
                 torch.cuda.set_device(ctx.device)
             lengths = ctx.lengths()
             if deflate:
                 pairs = all_pairs_deflate_hip(ctx, n, algorithm, lengths=lengths)
+            elif bzip2:
+                pairs = all_pairs_bzip2_hip(ctx, n, lengths=lengths)
             else:
                 pairs, singles = all_pairs_hip(ctx, n, lengths=lengths, with_singles=True)
         elif deflate:
@@ -375,6 +382,13 @@ def gpu_matrix(files, algorithm, reverse_complement, show_progress, save_directo
             if show_progress and n > tile:
                 starts = tqdm(starts, total=(n + tile - 1) // tile)
             pairs = (np.concatenate([ctx.deflate_pairs(algorithm, r0, min(n, r0 + tile)) for r0 in starts])
+                     if n else np.zeros((0, 0), np.uint32))
+        elif bzip2:
+            tile = max(1, (1 << 14) // max(n, 1))
+            starts = range(0, n, tile)
+            if show_progress and n > tile:
+                starts = tqdm(starts, total=(n + tile - 1) // tile)
+            pairs = (np.concatenate([ctx.bzip2_pairs(r0, min(n, r0 + tile)) for r0 in starts])
                      if n else np.zeros((0, 0), np.uint32))
         else:
             # row tiles so that --show-progress has something to show on large inputs; results are
@@ -469,7 +483,10 @@ def cli(sequences, fasta, directories, numThreads, compression, showProgress, sa
     # wanted (-s) or the reference's own thread-pool flow is asked for with SNACC_DEFLATE=stdlib
     deflate_on_gpu = (compression in ("gzip", "zlib") and saveCompression is None
                       and os.environ.get("SNACC_DEFLATE", "hip") != "stdlib")
-    if compression == "lz4" or deflate_on_gpu:
+    # bzip2 likewise, unless -s or SNACC_BZIP2=stdlib
+    bzip2_on_gpu = (compression == "bzip2" and saveCompression is None
+                    and os.environ.get("SNACC_BZIP2", "hip") != "stdlib")
+    if compression == "lz4" or deflate_on_gpu or bzip2_on_gpu:
         matrix = gpu_matrix(files, compression, reverse_complement, showProgress, saveCompression)
     else:
         matrix = threadpool_matrix(files, compression, numThreads, saveCompression, reverse_complement,

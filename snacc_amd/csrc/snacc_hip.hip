@@ -90,6 +90,8 @@ struct snk_ctx_impl {
     uint32_t *d_osave = nullptr;                                      // ... and its save areas, one per resident chain (beside d_ovf)
     // deflate add-on (snk_deflate.hip): opaque state + its destructor
     void *dfl = nullptr; void (*dfl_free)(void *) = nullptr;
+    // bzip2 add-on (snk_bzip2.hip): opaque state + its destructor
+    void *bz = nullptr; void (*bz_free)(void *) = nullptr;
     bool dfl_serial = false, dfl_kmer = true, dfl_norestart = false;
     uint8_t *d_bytes = nullptr, *d_packed = nullptr, *d_pmask = nullptr, *d_zero = nullptr;
     uint16_t *d_slots = nullptr;     // slot stream of the byte kernels (2 bytes per byte of the ASCII arena)
@@ -244,6 +246,8 @@ void free_sequences(snk_ctx_impl *c)
     c->n = 0; c->n_packed = 0; c->len.clear(); c->boff.clear(); c->is_packed.clear(); c->singles_done = false; c->single_have.clear();
     if (c->dfl && c->dfl_free) c->dfl_free(c->dfl);
     c->dfl = nullptr;
+    if (c->bz && c->bz_free) c->bz_free(c->bz);
+    c->bz = nullptr;
 }
 
 // ---- the 5-mer LUTs of the 2-bit kernel ---------------------------------------------------
@@ -777,6 +781,11 @@ void **snk_internal_dfl_slot(snk_ctx *c, void (***free_fn)(void *))
 {
     if (free_fn) *free_fn = &c->dfl_free;
     return &c->dfl;
+}
+void **snk_internal_bz_slot(snk_ctx *c, void (***free_fn)(void *))
+{
+    if (free_fn) *free_fn = &c->bz_free;
+    return &c->bz;
 }
 
 extern "C" {

@@ -66,6 +66,14 @@ def deflate_row_weights(lengths):
     return np.full(len(ln), ln.sum() + 1.0)
 
 
+def bzip2_row_weights(lengths):
+    """Work of row i of the bzip2 matrix: a pair job sorts the blocks of x_i's last block plus y_j (DESIGN.md
+    section 12), so a row costs sum_j (last(x_i) + len(y_j)), last = what x_i has behind its whole 900 k blocks."""
+    ln = np.asarray(lengths, dtype=np.float64)
+    last = np.where(ln > 899981, ln % 899981, ln)
+    return len(ln) * last + ln.sum() + 1.0
+
+
 def _die(what, exc):
     """A failed rendezvous or collective must end the run with a non-zero status and a message that says
     so -- never a silent single-rank result."""
@@ -249,3 +257,22 @@ def all_pairs_deflate_hip(ctx, n, algorithm, group=None, lengths=None):
     tile = max(1, (1 << 20) // max(n, 1))
     return all_pairs_sharded(n, rows_fn, group=group, device=dev, weights=weights, tile_rows=tile) \
         + np.uint32(DEFLATE[algorithm][1])
+
+
+def all_pairs_bzip2_hip(ctx, n, group=None, lengths=None):
+    """Sharded phase B of the bzip2 path: as :func:`all_pairs_deflate_hip`, rows weighted by the blocks they sort."""
+    import torch
+
+    dev = _torch_device(ctx)
+
+    def rows_fn(r0, r1):
+        out = torch.zeros((max(r1 - r0, 0), n), dtype=torch.int32, device=dev)
+        if dev.type == "cuda":
+            torch.cuda.current_stream(dev).synchronize()
+        ctx.bzip2_pairs_device(r0, r1, out.data_ptr(), None)
+        ctx.sync(None)
+        return out
+
+    weights = bzip2_row_weights(lengths) if lengths is not None else None
+    tile = max(1, (1 << 14) // max(n, 1))
+    return all_pairs_sharded(n, rows_fn, group=group, device=dev, weights=weights, tile_rows=tile)

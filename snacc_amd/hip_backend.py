@@ -25,6 +25,7 @@ EXPORTS = (
     "snk_pairs_device", "snk_pairs_list", "snk_frames_list", "snk_sync", "snk_last_pairs_ms", "snk_pairs_ms_log",
     "snk_fasta_extract", "snk_fasta_extract_many", "snk_fasta_last_error", "snk_free", "snk_upload_fasta", "snk_csv_rows_f64",
     "snk_deflate_prepare", "snk_deflate_singles", "snk_deflate_pairs", "snk_deflate_pairs_list", "snk_deflate_pairs_device", "snk_deflate_last_ms",
+    "snk_bzip2_prepare", "snk_bzip2_singles", "snk_bzip2_pairs", "snk_bzip2_pairs_list", "snk_bzip2_pairs_device", "snk_bzip2_last_ms",
 )
 
 #: deflate level and wrapper bytes behind the reference's gzip / zlib choices
@@ -148,6 +149,18 @@ def load():
     L.snk_deflate_pairs_device.argtypes = [vp, i32, i32, i32, vp, vp]
     L.snk_deflate_last_ms.restype = ctypes.c_double
     L.snk_deflate_last_ms.argtypes = [vp]
+    L.snk_bzip2_prepare.restype = i32
+    L.snk_bzip2_prepare.argtypes = [vp]
+    L.snk_bzip2_singles.restype = i32
+    L.snk_bzip2_singles.argtypes = [vp, vp]
+    L.snk_bzip2_pairs.restype = i32
+    L.snk_bzip2_pairs.argtypes = [vp, i32, i32, vp]
+    L.snk_bzip2_pairs_list.restype = i32
+    L.snk_bzip2_pairs_list.argtypes = [vp, i32, vp, vp]
+    L.snk_bzip2_pairs_device.restype = i32
+    L.snk_bzip2_pairs_device.argtypes = [vp, i32, i32, vp, vp]
+    L.snk_bzip2_last_ms.restype = ctypes.c_double
+    L.snk_bzip2_last_ms.argtypes = [vp]
     if L.snk_version() != ABI_VERSION:
         raise HipBackendError(f"ABI mismatch: library {L.snk_version()}, binding {ABI_VERSION}")
     _lib = L
@@ -376,6 +389,33 @@ class HipContext:
 
     def deflate_last_ms(self):
         return float(self._L.snk_deflate_last_ms(self._h))
+
+    # ---- bzip2 sizes (len(bz2.compress(..)), level 9) ----
+    def bzip2_singles(self):
+        out = np.zeros(self.n, dtype=np.uint32)
+        self._check(self._L.snk_bzip2_singles(self._h, out.ctypes.data), "snk_bzip2_singles")
+        return out
+
+    def bzip2_pairs(self, row_begin=0, row_end=None):
+        row_end = self.n if row_end is None else row_end
+        out = np.zeros((max(row_end - row_begin, 0), self.n), dtype=np.uint32)
+        self._check(self._L.snk_bzip2_pairs(self._h, row_begin, row_end, out.ctypes.data), "snk_bzip2_pairs")
+        return out
+
+    def bzip2_pairs_list(self, ij):
+        ij = np.ascontiguousarray(ij, dtype=np.int32).reshape(-1, 2)
+        out = np.zeros(len(ij), dtype=np.uint32)
+        self._check(self._L.snk_bzip2_pairs_list(self._h, len(ij), ij.ctypes.data, out.ctypes.data), "snk_bzip2_pairs_list")
+        return out
+
+    def bzip2_pairs_device(self, row_begin, row_end, d_ptr, stream=None):
+        """Rows [row_begin, row_end): sizes as u32 to device memory at `d_ptr`, the copy queued on `stream` (a hipStream_t
+        as int; None = the context's stream) and not waited for: call :meth:`sync` before reading them."""
+        self._check(self._L.snk_bzip2_pairs_device(self._h, row_begin, row_end, ctypes.c_void_p(d_ptr),
+                                                   ctypes.c_void_p(stream) if stream else None), "snk_bzip2_pairs_device")
+
+    def bzip2_last_ms(self):
+        return float(self._L.snk_bzip2_last_ms(self._h))
 
     def sync(self, stream=None):
         self._check(self._L.snk_sync(self._h, ctypes.c_void_p(stream) if stream else None), "snk_sync")

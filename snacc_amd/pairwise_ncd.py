@@ -11,7 +11,7 @@ fallback for it.  ``gzip`` and ``zlib`` sizes come from the HIP backend as well 
 N3), unless the compressed bytes themselves are wanted (``save_directory``) or the
 environment says ``SNACC_DEFLATE=stdlib`` (the reference's own call, asked for explicitly);
 ``lzma`` and ``bzip2`` are the stdlib calls the reference makes.  :func:`all_pairs` is the
-batched entry the CLI uses instead of N*N single calls (``lz4``, ``gzip``, ``zlib``).
+batched entry the CLI uses instead of N*N single calls (``lz4``, ``gzip``, ``zlib``, ``bzip2``).
 """
 import bz2
 import gzip
@@ -128,7 +128,7 @@ def compute_distance(x, y, cxy, cyx):
         return min((cxy - x) / x, (cyx - x) / x)
 
 
-GPU_ALGORITHMS = ("lz4", "gzip", "zlib")
+GPU_ALGORITHMS = ("lz4", "gzip", "zlib", "bzip2")
 
 _STDLIB = {"lzma": lzma.compress, "bzip2": bz2.compress, "gzip": gzip.compress, "zlib": zlib.compress}
 
@@ -153,8 +153,8 @@ def ncd(seq_i, seq_j, compressor="lz4"):
 def all_pairs(sequences, algorithm="lz4", ctx=None, rows=None):
     """Batched phase A + B of ref:snacc/cli.py:108-129 on the HIP backend.
 
-    sequences: list of ``bytes``/``str`` (already extracted); algorithm: ``lz4``, ``gzip`` or
-    ``zlib``.  Returns ``(singles, pairs)`` as int64 arrays *including* the getsizeof overhead
+    sequences: list of ``bytes``/``str`` (already extracted); algorithm: ``lz4``, ``gzip``, ``zlib``
+    or ``bzip2``.  Returns ``(singles, pairs)`` as int64 arrays *including* the getsizeof overhead
     (and, for gzip / zlib, the 18 / 6 wrapper bytes); ``rows=(r0, r1)`` restricts phase B to a
     row range (multi-GPU sharding)."""
     if algorithm not in GPU_ALGORITHMS:
@@ -168,6 +168,8 @@ def all_pairs(sequences, algorithm="lz4", ctx=None, rows=None):
         r0, r1 = rows if rows is not None else (0, len(sequences))
         if algorithm == "lz4":
             singles, pairs = ctx.singles(), ctx.pairs(r0, r1)
+        elif algorithm == "bzip2":
+            singles, pairs = ctx.bzip2_singles(), ctx.bzip2_pairs(r0, r1)
         else:
             singles, pairs = ctx.deflate_singles(algorithm), ctx.deflate_pairs(algorithm, r0, r1)
         singles = singles.astype(np.int64) + GETSIZEOF_OVERHEAD
